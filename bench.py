@@ -12,7 +12,11 @@ frames on each GPU per batch) on each of two streams (`--streams`) are the defau
 reference's own: one frame at a time).  Frame-batch data parallelism: every rank processes K frames of its own (weak scaling) and the
 per-frame results are gathered to rank 0 with ONE collective inside the timed region.  Rank 0 prints one JSON line.
 
-Three precision modes are timed by a default run (N = 1):
+A plain run does only what the headline needs: it sets up, warms up, times exactly K steps (one repeat), writes the last timed forward()'s
+outputs if `--dump-outputs DIR` is given, and prints the line (`value`, `ms_per_step`, `p50_ms` of the headline mode; the objects below
+are null or absent).  `--full` adds everything else: R repeats, the graph-replay-equals-eager check, the roofline sample and the objects below.
+
+Three precision modes are timed by a `--full` run (N = 1):
   value / ms_per_step / p50_ms   `--dtype split` (default): the fp32-grade mode -- every GEMM and convolution on (hi, lo) fp16 operand pairs (three
                 v_mfma_f32_16x16x32_f16 per product), fp32 accumulate, fp32 tensors in the DSVT stage.  The reference's arithmetic is fp32
                 (include/params.h:332); ALL NINE box columns (yaw included) sit within 1e-3 of the fp32 oracle on every check cloud (measured ~1e-4 worst):
@@ -26,8 +30,8 @@ Three precision modes are timed by a default run (N = 1):
                 (seeds 21, 9, 3, 1, 0, 7, 16, 23), per column and over all nine, run through the timed pipelines.
   targets       which operating point meets which bar (>= 200 frames/s; <= 5 ms p50 per frame), and whether one point meets both.
 
-Timing: K steps per repeat, every repeat between two torch.cuda.synchronize() on every rank; R = max(3, min(15, ceil(300 / K))) repeats (a function
-of K only).  Collectives: one all-gather of the ranks' device identities at start-up (n_gpus = DISTINCT devices, checked), one barrier before the first
+Timing: K steps per repeat, every repeat between two torch.cuda.synchronize() on every rank; one repeat, or with `--full` R = max(3, min(15, ceil(300 / K)))
+repeats (a function of K only).  Collectives: one all-gather of the ranks' device identities at start-up (n_gpus = DISTINCT devices, checked), one barrier before the first
 repeat, the RESULT GATHER AFTER EVERY BATCH (one forward on every rank = frames_per_forward frames per rank: configs[3]'s 32 frames over 8 GPUs; `--gather-every-batch`, the default
 whenever a communicator exists: N > 1 and `--rccl-single`) inside every repeat -- the product loop of BASELINE configs[3], buffers allocated once (round 5
 gathered once, in the last repeat: `--gather-once`) --, rank 0 checks its own rows in the gathered tensor bit for bit, one barrier after the last repeat, ONE
@@ -35,7 +39,7 @@ all-gather of the R per-repeat times (`repeat_values_per_rank`); `value` = total
 every N, so N = 8 / N = 1 compares like with like (a communicator-free N = 1 run has no collective to time: `gathers_per_repeat` says which it was).  The roofline sample (one eager forward with HIP events around every launch) is a pre-pass
 outside every timed region.
 
-Extra objects in the line:
+Extra objects in the line (`--full`):
   single_frame_mode  (N = 1) the same kernels with ONE frame per forward and one in flight -- the reference's own mode: frames/s and p50, both modes.
   host_input_mode    (N = 1) the reference's own timed bracket (src/dsvt-ai-trt.cpp:1918-1956): upload from pinned host memory + the frame + download
                 of the final boxes, one frame at a time, host clock around each frame -- the PCIe-inclusive figure, never `value`.
@@ -416,8 +420,8 @@ class ModeRun:
                         self.run_frame(i * self.NS + s, self.scratch[s])
                 torch.cuda.synchronize()
         # the graph replay does the frame's work: one replay against one eager (op-by-op) run of the same frame, bit for bit
-        # (every kernel is deterministic), outside the timed region
-        if self.use_graph:
+        # (every kernel is deterministic), outside the timed region (--full)
+        if self.use_graph and a.full:
             ok = True
             for s in range(self.NS):
                 with torch.cuda.stream(self.streams[s]):
@@ -498,7 +502,7 @@ class ModeRun:
         collective rounds however many repeats, because on this stack (ROCm 7.2, RCCL 2.26 of torch 2.10) a third barrier / gather / barrier /
         all-reduce round interleaved with HIP-graph replays ends in "Memory access fault ... write access to a read-only page" (DESIGN 5).
         Every repeat is bracketed by torch.cuda.synchronize() on both sides; value = median over the repeats of total frames / max-over-ranks time."""
-        R = self.args.repeats if self.args.repeats > 0 else max(3, min(MAX_REPEATS, -(-300 // K)))
+        R = self.args.repeats if self.args.repeats > 0 else max(3, min(MAX_REPEATS, -(-300 // K))) if self.args.full else 1
         self.par.barrier(); torch.cuda.synchronize()
         dts, fms, gathered, gather_ms = [], [], None, None
         for r in range(R):
@@ -703,7 +707,15 @@ def main():
                     help="the result gather runs after EVERY batch (one forward per stream on every rank) inside every repeat, with buffers allocated once -- the product loop of "
                          "BASELINE configs[3]; default for N > 1 and with --rccl-single.  --gather-once: round 5's protocol (the gather inside the last repeat only)")
     ap.add_argument("--gather-once", dest="gather_every_batch", action="store_false")
-    ap.add_argument("--repeats", type=int, default=0, help="repeats of the K-step timed loop (0 = max(3, min(15, ceil(300 / K))): a function of K only, so every rank runs the same number)")
+    ap.add_argument("--repeats", type=int, default=0, help="repeats of the K-step timed loop (0 = one, so that exactly K steps are timed; with --full max(3, min(15, ceil(300 / K))): "
+                                                           "a function of K only, so every rank runs the same number)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: repeats, the graph-replay-equals-eager check, the roofline sample, the other "
+                                                        "precision modes, single_frame_mode / host_input_mode, targets, other_configs, cpp_host_mode, cpu_baseline "
+                                                        "(the --no-* switches below select among them).  Without it a run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the headline mode's last timed forward() returned as DIR/boxes.npy ([frames_per_forward, 500, 9] float32) and "
+                         "DIR/box_counts.npy ([frames_per_forward] float32); rows at or past a frame's count are zeroed (never written by the forward); "
+                         "the inputs are seeded, so the same arguments give the same inputs")
     ap.add_argument("--dump-rows", default=None, help="rank 0 saves the gathered result rows [K * N, 4501] of the headline mode as .npy (tests: the gather against single-process rows)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip other_configs (BASELINE configs[1] and configs[4] timed beside the headline, ~10 s)")
     ap.add_argument("--no-cpp-host", action="store_true", help="skip cpp_host_mode (the C++ host dsvt_detect on the same clouds: writes an ~80 MB .wts file, ~25 s)")
@@ -782,14 +794,14 @@ def main():
         """build, warm, capture and time one precision mode; returns its part of the JSON line (rank 0) or None"""
         run = ModeRun(pkg, par, args, mode, dev, caps, FB, weights, pool, host_pool, world, rank)
         run.prepare()
-        # device-side counts of each pooled forward (for the algorithmic byte / flop counts), read outside the timed region
+        # device-side counts of each pooled forward (for the algorithmic byte / flop counts), read outside the timed region (--full)
         counts = []
-        for pts, n in pool:
+        for pts, n in (pool if args.full else []):
             st = run.pipes[0].voxel_stage(pts, n)
             counts.append(dict(P=int(st["P"][0]), Nk=int(st["Nk"][0]), S=[int(g[2][0]) for g in st["gss"]]))
         torch.cuda.synchronize()
         prof = None
-        if not args.no_kernel_events:
+        if args.full and not args.no_kernel_events:
             prof = {k: [] for k in ("DsvtLinearPlugin", "DsvtEncoderMlpPlugin", "DsvtSetAttentionPlugin", "DsvtConv2dPlugin", "DsvtPillarFeatureNetPlugin",
                                     "DsvtPosEmbedPlugin", "Points2FeaturesPlugin", "DsvtSetPartitionPlugin", "Map2BevPlugin")}
         # warm-up of the one collective: RCCL sets up its channels lazily at the first call of each kind (tens of ms: measured 45 ms on a size-1
@@ -818,7 +830,7 @@ def main():
                    gather_ms=None if gather_ms is None or not run.collective else round(gather_ms, 3),
                    value_of_the_repeat_with_the_gather=round(total / dts[-1], 3),
                    gathers_per_repeat=(K // FB) if (run.collective and args.gather_every_batch) else (1 if run.collective else 0),
-                   graph_replay_equals_eager=run.replay_equals_eager, frame0=counts[0], gather_own_rows_bit_identical=own_ok,
+                   graph_replay_equals_eager=run.replay_equals_eager, frame0=counts[0] if counts else None, gather_own_rows_bit_identical=own_ok,
                    repeat_values_per_rank=[[round(K / d, 1) for d in pr] for pr in getattr(run, "per_rank_dts", [])] if world > 1 else None)
         out["_run"] = run
         if prof is not None and sampled:
@@ -839,6 +851,17 @@ def main():
         return out
 
     head = run_mode(args.dtype)
+    if rank == 0 and args.dump_outputs:
+        # what the last timed forward() returned (its FB frames: rows K - FB .. K - 1 of the result buffer, an exact copy of the pipeline's
+        # boxes and count), written before any --full leg reuses the buffer.  Rows at or past a frame's count are zeroed: the NMS kernel writes
+        # only the kept rows (no zero fill), so the rest hold whatever earlier frames or allocations left there, not output of this forward
+        last = results[K - FB:K].cpu().numpy()
+        counts = np.ascontiguousarray(last[:, par.ROW - 1], dtype=np.float32)
+        boxes = np.array(last[:, :par.ROW - 1].reshape(FB, 500, 9), dtype=np.float32)
+        boxes[np.arange(500)[None, :] >= counts[:, None]] = 0.0
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "boxes.npy"), boxes)
+        np.save(os.path.join(args.dump_outputs, "box_counts.npy"), counts)
     if rank == 0:
         run = head.pop("_run")
         line = {
@@ -888,7 +911,7 @@ def main():
     # the clouds every timed mode is CHECKED on against the CPU oracle (cpu_baseline.box_err_vs_oracle): eight seeds, the 24-cloud sweep's worst yaw
     # cases among them (21, 9, 3, 1: profiles/r04_mx_box_sweep.txt), run through the timed pipelines themselves (FB frames per forward)
     CHECK_SEEDS = [21, 9, 3, 1, 0, 7, 16, 23][:max(1, args.oracle_clouds)] if args.oracle_clouds > 0 else []
-    check_clouds = [(sd, pkg.synth.lidar_like(args.points, seed=sd)) for sd in CHECK_SEEDS] if (rank == 0 and world == 1 and not args.no_cpu_baseline) else []
+    check_clouds = [(sd, pkg.synth.lidar_like(args.points, seed=sd)) for sd in CHECK_SEEDS] if (rank == 0 and world == 1 and args.full and not args.no_cpu_baseline) else []
 
     def fb_rows(run_, tag):
         """FilterBoxByScore rows (before NMS: the reference engine's output) of the check clouds in this mode, through the timed pipeline"""
@@ -909,7 +932,7 @@ def main():
         mode_rows[tag] = rows_
         pipe.nms = nms_op
 
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         if not args.no_cpu_baseline:
             fb_rows(run, args.dtype)
         other = {"split": "f16", "f16": "split"}.get(args.dtype)
